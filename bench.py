@@ -7,11 +7,16 @@ ViT encoder -> 29 KV-cached greedy decode steps -> (N>1) one RCCL all-gather of 
 the reference's batch-global stop rule.  Launch as
   python bench.py [--gpus 1 --steps K --warmup W]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
-Rank 0 prints ONE JSON line.  `roofline` is the dominant kernel's algorithmic rate measured
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the line;
+`--dump-outputs DIR` also writes what the last timed step returned (DIR/<name>.npy, float32), so two
+builds can be compared output for output (weights, images and uniforms are seeded: the same arguments
+give the same inputs).  `roofline` is the dominant kernel's algorithmic rate measured
 with HIP events around each of its launches inside the timed region; its `traffic` is the HBM-side
 bytes per launch of that kernel from the committed rocprofv3 PMC summary (tools/pmc_bench.sh:
-FETCH_SIZE x 2 + WRITE_SIZE, the gfx950 correction) when one exists for it; `cpu_baseline` times
-the CPU oracle (fp32 restatement of the reference algorithm, full-prefix recompute) on the host.
+FETCH_SIZE x 2 + WRITE_SIZE, the gfx950 correction) when one exists for it.  `--full` adds the legs
+that take runs of their own, after the timed steps: `cpu_baseline` times
+the CPU oracle (fp32 restatement of the reference algorithm, full-prefix recompute) on the host, and
+`config.multi_gpu_check` decodes one more batch to verify the stop rule on the gathered ids.
 `--model grid` measures config 3 (ResNet-101 trunk as HIP MFMA GEMMs over NHWC planes, then the
 HIP encoder tail and decode loop; `--torch-trunk` runs the trunk through PyTorch/MIOpen fp32 instead); `--mode scst` measures config 5's reward step
 (encode once, HIP sample on injected uniforms + HIP greedy baseline from the same memory, all-gather
@@ -142,6 +147,25 @@ def cpu_baseline(seconds: float, batch: int, max_len: int) -> dict:
     return out
 
 
+# the array a caller of the timed step receives, per mode (--dump-outputs)
+OUTPUT_NAME = {"greedy": "caption_ids", "beam": "beam_ids", "scst": "reward_advantage"}
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory: str, mode: str, out: torch.Tensor) -> None:
+    """DIR/<name>.npy, float32: greedy - the captions after the stop rule, (global batch, output_len) token ids;
+    beam - the best beam's ids; scst - sampled minus greedy CIDEr-D reward per image.  Token ids are exact in
+    float32 (vocabulary < 2^24).  An output over the size limit is cut to a fixed seeded sample of its elements."""
+    import numpy as np
+
+    a = out.detach().to("cpu").to(torch.float32).contiguous().numpy()
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(a.size, DUMP_LIMIT_BYTES // 4, replace=False))
+        a = a.reshape(-1)[keep]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, OUTPUT_NAME[mode] + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -153,7 +177,12 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--cpu-batch", type=int, default=16,
                     help="images per oracle call of the CPU baseline sample (a slice of the B = 256 workload)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs the headline figure does not need: the CPU baseline "
+                         "(cpu_baseline) and the stop-rule self-check on one more decoded batch (config.multi_gpu_check)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32; rank 0)")
     ap.add_argument("--no-graphs", action="store_true", help="launch the decode loop eagerly (no hipGraph)")
     ap.add_argument("--decode-chains", type=int, default=0,
                     help="independent decode chains per batch (icap_set_decode_chains; 0 = library default)")
@@ -358,10 +387,12 @@ def main():
         }
         if pipe_ev:
             phases["overlapped"] = True  # encoder and decode ms of one batch; consecutive batches' phases overlap
-    # multi-GPU self-check: the stop rule on the gathered ids equals the all-reduce form of SURVEY.md §8(e)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, args.mode, out)
+    # multi-GPU self-check (--full): the stop rule on the gathered ids equals the all-reduce form of SURVEY.md §8(e)
     # (each rank's per-column "every row ended" mask AND-reduced over ranks), so the line can be verified alone
     stop_check = None
-    if args.mode == "greedy":
+    if args.full and args.mode == "greedy":
         mem = encode()
         ids, _ = eng.greedy_raw(mem, W.START_TOKEN, W.END_TOKEN, L)
         col = (ids[:, 1:] == W.END_TOKEN).all(dim=0).to(torch.int32)
@@ -422,7 +453,7 @@ def main():
         cpu = None
         if roof["traffic"] is not None:
             roof["traffic_unit"] = f"bytes/launch (HBM-side, rocprofv3 PMC, {traffic_source(workload)})"
-        if ws == 1 and not args.no_cpu_baseline and args.model == "vit":
+        if args.full and ws == 1 and not args.no_cpu_baseline and args.model == "vit":
             cpu = cpu_baseline(args.cpu_seconds, args.cpu_batch, L)
         line = {
             "metric": {"greedy": METRIC, "scst": "images/sec, SCST reward step (sample + greedy + CIDEr-D)",

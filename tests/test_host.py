@@ -263,3 +263,21 @@ def test_data_parallel_gather_matches_single_process():
     mem_all = torch.from_numpy(np.random.Generator(np.random.PCG64(3)).standard_normal((total, 20, 512)).astype(np.float32))
     ref = O.greedy_from_memory(sd, mem_all, W.START_TOKEN, W.END_TOKEN, 6)
     assert np.array_equal(got, ref.numpy())
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the last step's result lands as DIR/<name>.npy in float32 with token ids exact; an
+    output over the size limit is cut to the same seeded sample on every call."""
+    import bench
+
+    ids = torch.randint(0, W.VOCAB_SIZE, (7, 30))
+    bench.dump_outputs(str(tmp_path / "a"), "greedy", ids)
+    got = np.load(tmp_path / "a" / "caption_ids.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, ids.numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 40)
+    r = torch.arange(100, dtype=torch.float64)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), "scst", r)
+    b, c = (np.load(tmp_path / d / "reward_advantage.npy") for d in ("b", "c"))
+    assert b.dtype == np.float32 and b.shape == (10,) and np.array_equal(b, c)
+    assert len(set(b.tolist())) == 10 and set(b.tolist()) <= set(range(100))

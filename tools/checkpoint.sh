@@ -9,7 +9,7 @@ timeout -k 10 500 python -u -m pytest tests -m gpu -x -q -s --timeout 120 --time
 tail -1 $O/${T}_tests.log; grep "greedy vs oracle" $O/${T}_tests.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/${T}_smoke.log 2>&1 || { tail -20 $O/${T}_smoke.log; exit 1; }
 tail -2 $O/${T}_smoke.log
-timeout -k 10 400 python bench.py > $O/${T}_vit.json 2> $O/${T}_vit.err || { tail -20 $O/${T}_vit.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/${T}_vit.json 2> $O/${T}_vit.err || { tail -20 $O/${T}_vit.err; exit 1; }
 tail -1 $O/${T}_vit.json
 timeout -k 10 300 python bench.py --model grid --no-cpu-baseline > $O/${T}_grid.json 2> $O/${T}_grid.err || { tail -20 $O/${T}_grid.err; exit 1; }
 tail -1 $O/${T}_grid.json

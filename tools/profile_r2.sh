@@ -12,7 +12,7 @@ mkdir -p $O
 bash tools/pmc_bench.sh $T > $O/${T}_pmc.log 2>&1 || { tail -20 $O/${T}_pmc.log; exit 1; }
 cp gpurun_out/pmcb_$T/traffic.json profiles/r02/pmc_traffic.json
 cp gpurun_out/pmcb_$T/traffic.json $O/${T}_pmc_traffic.json
-timeout -k 10 300 python bench.py > $O/${T}_bench.json 2> $O/${T}_bench.err || { tail -20 $O/${T}_bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full > $O/${T}_bench.json 2> $O/${T}_bench.err || { tail -20 $O/${T}_bench.err; exit 1; }
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$T -o run -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/prof_$T.log 2>&1 || exit 1
 f=$(find $O/prof_$T -name "*kernel_trace.csv" | head -1)
 python tools/trace_decode.py $f > $O/${T}_trace.txt 2>&1
